@@ -1,7 +1,13 @@
 #!/usr/bin/env python
 """Benchmark of the MFP train-step hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config c2|c3|c4|c5]
+    python bench.py --gpus N --steps K --warmup W [--config c2|c3|c4|c5] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the line: the headline figure and nothing else.  `--full`
+adds the checks and extra measurements described below (the median pass, the bf16 / fp8 deviations, the roofline, c5's
+fp8 mode, the CPU baseline); `--no-roofline` / `--no-cpu-baseline` leave legs of it out.  `--dump-outputs DIR` writes
+what the last timed step handed its caller to DIR/<name>.npy (see dump_outputs); the inputs are seeded, so two builds
+run with the same arguments can be compared output for output.
 
 Metric (BASELINE.json): elements/sec of the train step (masking -> forward -> masked losses ->
 backward -> [RCCL all-reduce] -> clipnorm + L2 + Keras Adam) on Crello-shaped synthetic batches.
@@ -24,14 +30,15 @@ N grows = weak scaling):
       oracle, kept as a precision-only mode (`--dtype fp8` times it alone)
 
 Timed region: K hipGraph replays of the captured step between two device synchronisations (+ barriers for N > 1);
-`value` = elements of all ranks / that wall time; `ms_per_step_median` = median of the per-step HIP-event intervals of
-a second pass over the same K steps (SURVEY.md section 8d asks for the median; an event between two graph launches
-costs ~5 us of queue time, so the events stay out of the timed region; the two agree within that).  The loop ROTATES
+`value` = elements of all ranks / that wall time, `ms_per_step` = that wall time / K; `ms_per_step_median` (`--full`) =
+median of the per-step HIP-event intervals of a second pass over the same K steps (SURVEY.md section 8d asks for the
+median; an event between two graph launches costs ~5 us of queue time, so the events stay out of the timed region; the
+two agree within that).  The loop ROTATES
 `--resident` (default 4) input batches that sit in HBM, each with its own capture of the same step: 4 x 136 MB of f32
 embeddings do not fit the 256 MB infinity cache, so every step's inputs are read from HBM like a loader-fed run's
 (`input_residency` on the line; `--resident 1` = the single re-masked batch of rounds 1-3).
 
-Extra objects on the line (prompt section 4):
+Extra objects on the line (prompt section 4; roofline, cpu_baseline, fp8_mode and the deviations with `--full` only):
   roofline     - the kernel FAMILY with the largest summed duration in a step.  Durations: the tracer's device times
                  (torch.profiler = roctracer) of the step AS TIMED (hipGraph replay), reported raw
                  (`avg_launch_us_traced`, `frac_traced`) and normalised so that the families sum to the timed step
@@ -114,6 +121,9 @@ def parse():
     ap.add_argument("--seq", type=int, default=None, help="positions per document (override; 64 = two documents per 128-row "
                     "tile, the shape of real Crello / RICO batches whose sequences are at most 51 positions long)")
     ap.add_argument("--resident", type=int, default=4, help="input batches resident in HBM that the timed loop rotates")
+    ap.add_argument("--full", action="store_true", help="also run the checks and extra measurements (median pass, deviations, "
+                    "roofline, c5 fp8 mode, CPU baseline); off: only what the headline figure needs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -335,6 +345,29 @@ def oracle_deviation(ic, cfg, device, dtype="bf16", B=4, mixes=("random",)):
                             "fields -- attribution of the deviation by rounding site: profiles/r06_bf16_error_budget.txt" % (B, S, D, L)}
 
 
+DUMP_MAX_BYTES = 48 * 10 ** 6      # (.npy headers aside)
+
+
+def dump_outputs(out_dir, model, sums, loss):
+    """What the last timed step handed its caller, as float32 / float64 .npy files of at most DUMP_MAX_BYTES in all:
+      loss_sums - the [nkeys][3] tensor train_step returned (per loss key: loss, score numerator, score denominator)
+      loss      - the total loss of the line's final_loss (sum of the per-key losses + the L2 term of the parameters)
+      params    - the flat f32 parameter buffer its Adam update left; beyond the byte budget `params_sample` instead: the
+                  entries at a fixed sorted index set drawn from numpy's default_rng(0) (the same for every build)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss_sums": sums.detach().float().cpu().numpy(), "loss": np.array([loss], dtype=np.float64)}
+    w = model.model.store.w.detach().float().cpu().numpy()
+    room = (DUMP_MAX_BYTES - sum(a.nbytes for a in arrays.values())) // w.itemsize
+    if w.size <= room:
+        arrays["params"] = w
+    else:
+        idx = np.sort(np.random.default_rng(0).choice(w.size, room, replace=False))
+        arrays["params_sample"] = w[idx]
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -373,8 +406,9 @@ def main():
 
     ic = make_input_columns(cfg.get("dataset", "crello"))
     batch = synthetic_batch(ic, B, S, seed=rank, ragged=False, device=device)
+    roofline = args.full and not args.no_roofline     # (the deviation legs ride with the roofline, as they always did)
     extra = {}
-    if dtype in ("bf16", "fp8") and rank == 0 and not args.no_roofline:
+    if roofline and dtype in ("bf16", "fp8") and rank == 0:
         extra = bf16_deviation(ic, cfg, batch, masking_method, device, dtype)
         if cfg.get("dataset", "crello") == "crello":
             try:
@@ -437,23 +471,28 @@ def main():
     torch.cuda.synchronize()
     barrier()
     elapsed = time.perf_counter() - t0
-    # the median of per-step intervals: a SECOND pass of the same K steps with an event between consecutive steps (an
-    # event record between two graph launches costs ~5 us of queue time per step: not inside the timed region above)
-    marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
-    marks[0].record()
-    for i in range(args.steps):
-        model.train_step(batches[i % len(batches)])
-        marks[i + 1].record()
-    torch.cuda.synchronize()
-    barrier()
-    per_step = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
-    median_ms = per_step[len(per_step) // 2] if len(per_step) % 2 else 0.5 * (per_step[len(per_step) // 2 - 1] + per_step[len(per_step) // 2])
+    # what the last timed step computed, read before anything else steps the model
+    metrics = model.metrics_dict(sums)
+    assert metrics["loss"] == metrics["loss"] and abs(metrics["loss"]) < 1e9, "loss is not finite"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, sums, metrics["loss"])
+    median_ms = None
+    if args.full:
+        # the median of per-step intervals: a SECOND pass of the same K steps with an event between consecutive steps (an
+        # event record between two graph launches costs ~5 us of queue time per step: not inside the timed region above)
+        marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
+        marks[0].record()
+        for i in range(args.steps):
+            model.train_step(batches[i % len(batches)])
+            marks[i + 1].record()
+        torch.cuda.synchronize()
+        barrier()
+        per_step = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
+        median_ms = per_step[len(per_step) // 2] if len(per_step) % 2 else 0.5 * (per_step[len(per_step) // 2 - 1] + per_step[len(per_step) // 2])
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    metrics = model.metrics_dict(sums)
-    assert metrics["loss"] == metrics["loss"] and abs(metrics["loss"]) < 1e9, "loss is not finite"
     in_sync = True
     dp_info = None
     if world > 1:   # replicas must hold identical parameters after identical averaged updates
@@ -479,7 +518,7 @@ def main():
     out = {
         "metric": "elements_per_sec_train_step", "value": value, "unit": "elements/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": 1e3 * elapsed / args.steps, "ms_per_step_median": median_ms,
+        "ms_per_step": 1e3 * elapsed / args.steps,
         "higher_is_better": True, "scaling": "weak",
         "vs_baseline": None, "dtype": {"bf16": "bf16", "fp32": "f32", "fp8": "fp8 (MX e4m3 + e8m0 per 32: QKV/FFN1 forward products; bf16 elsewhere)"}[dtype],
         "data": "synthetic",
@@ -497,6 +536,8 @@ def main():
                             if len(batches) > 1 else "one batch, re-masked every step (its inputs can sit in the infinity cache)"),
         "fused_path": bool((dtype in ("bf16", "fp8") and D == 256 and (S == 128 or (S == 64 and B % 2 == 0))) or (dtype == "bf16" and D == 512)),
     }
+    if median_ms is not None:
+        out["ms_per_step_median"] = median_ms
     if dp_info is not None:
         out["dp"] = dp_info
     out.update(extra)
@@ -506,12 +547,12 @@ def main():
     # calls of instrumented eager steps of the same workload (HIP events on the launch stream; the fallback for the
     # durations when the tracer is unavailable)
     eager_recs, replay = None, None
-    if not args.no_roofline and rank == 0 and graphed and world == 1:
+    if roofline and rank == 0 and graphed and world == 1:
         try:
             replay = replay_kernel_times(model, batch)
         except Exception as exc:   # measurement aid: never fail the bench line over it
             print("bench.py: tracer unavailable (%s); event-timed eager durations" % exc, file=sys.stderr)
-    if not args.no_roofline:
+    if roofline:
         # instrumented eager steps (HIP events around the library calls): EVERY rank steps -- with N > 1 an eager step
         # all-reduces the gradients, so rank 0 alone would wait for its peers forever -- rank 0 reports
         model._graph = None
@@ -522,7 +563,7 @@ def main():
             model.train_step(batches[0])
         eager_recs = (ops.stop_profile(), 3)
         barrier()
-    if not args.no_roofline and rank == 0:
+    if roofline and rank == 0:
         recs, nprof = eager_recs
         agg, blk, blk_ms = {}, [0.0, 0.0, 0.0], {}
         for name, flops, nbytes, ms, scope, share in recs:      # share < 1: one launch booked under several scopes
@@ -614,7 +655,7 @@ def main():
         except Exception as exc:   # measurement aid only: never fail the bench line over it
             roof["measured_peaks"] = "unavailable: %s" % exc
         out["roofline"] = roof
-    if args.config == "c5" and dtype == "bf16" and world == 1 and not args.no_roofline:
+    if roofline and args.config == "c5" and dtype == "bf16" and world == 1:
         # BASELINE config 5 names fp8: the precision-only mode's figures beside the bf16 line (same command, --dtype fp8)
         try:
             del model
@@ -630,7 +671,7 @@ def main():
                                        "e4m3 WEIGHT rounding and is outside north_star's 1e-3"}
         except Exception as exc:
             out["fp8_mode"] = "unavailable: %s" % exc
-    if not args.no_cpu_baseline and rank == 0 and world == 1:
+    if args.full and not args.no_cpu_baseline and rank == 0 and world == 1:
         out["cpu_baseline"] = cpu_baseline(ic, cfg)
     if rank == 0:
         print(json.dumps(out), flush=True)

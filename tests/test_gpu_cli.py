@@ -154,7 +154,7 @@ def test_bench_two_ranks_on_one_gpu_over_gloo():
     env = dict(os.environ, MFP_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
-           "--config", "c4", "--batch", "16"]
+           "--config", "c4", "--batch", "16", "--full"]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=420)
     assert res.returncode == 0, res.stderr[-2000:]
     line = json.loads(res.stdout.strip().splitlines()[-1])

@@ -12,11 +12,11 @@ STEPS=6 bash tools/pmc_step.sh > $O/r02_pmc_step.log 2>&1 || true
 cp $O/pmc_step/pmc_traffic.json $O/r02_pmc_traffic.json
 cp $O/pmc_step/summary.txt $O/r02_pmc_traffic_summary.txt
 mkdir -p profiles && cp $O/r02_pmc_traffic.json profiles/r02_pmc_traffic.json     # bench.py reads it from profiles/
-python bench.py --steps 100 --warmup 10 2>/dev/null | tail -1 > $O/r02_bench_c2.json
-python bench.py --steps 100 --warmup 10 --config c3 --no-cpu-baseline 2>/dev/null | tail -1 > $O/r02_bench_c3.json
-python bench.py --steps 30 --warmup 5 --config c5 --no-cpu-baseline 2>/dev/null | tail -1 > $O/r02_bench_c5_fp8.json
-python bench.py --steps 30 --warmup 5 --config c5 --dtype bf16 --no-cpu-baseline 2>/dev/null | tail -1 > $O/r02_bench_c5_bf16.json
-python bench.py --steps 100 --warmup 10 --config c4 --no-cpu-baseline --no-roofline 2>/dev/null | tail -1 > $O/r02_bench_c4_1gpu.json
+python bench.py --full --steps 100 --warmup 10 2>/dev/null | tail -1 > $O/r02_bench_c2.json
+python bench.py --full --steps 100 --warmup 10 --config c3 --no-cpu-baseline 2>/dev/null | tail -1 > $O/r02_bench_c3.json
+python bench.py --full --steps 30 --warmup 5 --config c5 --no-cpu-baseline 2>/dev/null | tail -1 > $O/r02_bench_c5_fp8.json
+python bench.py --full --steps 30 --warmup 5 --config c5 --dtype bf16 --no-cpu-baseline 2>/dev/null | tail -1 > $O/r02_bench_c5_bf16.json
+python bench.py --full --steps 100 --warmup 10 --config c4 --no-cpu-baseline --no-roofline 2>/dev/null | tail -1 > $O/r02_bench_c4_1gpu.json
 head -40 $O/r02_kernel_stats.csv; tail -3 $O/r02_pmc_traffic_summary.txt; python -c "
 import json
 for n in ('c2','c3','c5_fp8','c5_bf16','c4_1gpu'):

@@ -19,11 +19,11 @@ rm -rf $O/pmc_step/FETCH_SIZE $O/pmc_step/WRITE_SIZE
 mkdir -p profiles && cp $O/r03_pmc_traffic.json profiles/r03_pmc_traffic.json     # bench.py reads it from profiles/
 TAG=r03 STEPS=6 bash tools/pmc_mfma.sh > $O/r03_pmc_mfma.log 2>&1 || true
 rm -rf $O/pmc_mfma
-python bench.py --steps 100 --warmup 10 2>/dev/null | tail -1 > $O/r03_bench_c2.json
-python bench.py --steps 100 --warmup 10 --config c3 --no-cpu-baseline 2>/dev/null | tail -1 > $O/r03_bench_c3.json
-python bench.py --steps 100 --warmup 10 --config c4 --no-cpu-baseline 2>/dev/null | tail -1 > $O/r03_bench_c4_1gpu.json
-python bench.py --steps 30 --warmup 5 --config c5 --no-cpu-baseline 2>/dev/null | tail -1 > $O/r03_bench_c5_fp8.json
-python bench.py --steps 30 --warmup 5 --config c5 --dtype bf16 --no-cpu-baseline 2>/dev/null | tail -1 > $O/r03_bench_c5_bf16.json
+python bench.py --full --steps 100 --warmup 10 2>/dev/null | tail -1 > $O/r03_bench_c2.json
+python bench.py --full --steps 100 --warmup 10 --config c3 --no-cpu-baseline 2>/dev/null | tail -1 > $O/r03_bench_c3.json
+python bench.py --full --steps 100 --warmup 10 --config c4 --no-cpu-baseline 2>/dev/null | tail -1 > $O/r03_bench_c4_1gpu.json
+python bench.py --full --steps 30 --warmup 5 --config c5 --no-cpu-baseline 2>/dev/null | tail -1 > $O/r03_bench_c5_fp8.json
+python bench.py --full --steps 30 --warmup 5 --config c5 --dtype bf16 --no-cpu-baseline 2>/dev/null | tail -1 > $O/r03_bench_c5_bf16.json
 head -30 $O/r03_kernel_stats.csv; tail -3 $O/r03_pmc_traffic_summary.txt; tail -25 $O/r03_pmc_mfma_lds.txt; python -c "
 import json
 for n in ('c2','c3','c4_1gpu','c5_fp8','c5_bf16'):

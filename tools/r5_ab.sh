@@ -2,7 +2,7 @@
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 V=$1; shift
 for rep in 1 2; do for v in 1 0; do
-  env $V=$v python bench.py $@ --no-cpu-baseline --no-roofline 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$V=$v', round(d['ms_per_step'],4), round(d['ms_per_step_median'],4))"
+  env $V=$v python bench.py --full $@ --no-cpu-baseline --no-roofline 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$V=$v', round(d['ms_per_step'],4), round(d['ms_per_step_median'],4))"
 done; done
 OUT=gpurun_out/prof_ab; rm -rf $OUT; mkdir -p $OUT
 for v in 1 0; do
